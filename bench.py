@@ -6,13 +6,19 @@ with --gpus N the same cohort is sharded over N ranks = configs[3], strong scali
 The genotype panel, P and Py are resident in HBM before the timed region; the step
 includes the screen, the exact fp64 refine of the candidates and the hit collection.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  Extra objects: roofline (the int8 screen kernel, measured
-with HIP events inside libgmat_hip on its launch stream), cpu_baseline (the oracle's
-numpy restatement of the reference per-row loop on a bounded row sample, rank 0, N=1),
-grm (configs[1]: agmat GRM on 2,000 x 20,000, GFLOP/s dense-equivalent 2n^2m).
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step) with the roofline of the timed steps' own kernel accounting (HIP
+events inside libgmat_hip on the launch streams; no run of its own).  --dump-outputs DIR writes
+the last timed step's hits (merged over the ranks, sorted by (i, j)) as DIR/<name>.npy.
+--full adds every other leg, each with its --no-* switch: the full-triangle check against the
+recorded exhaustive hit set, cpu_baseline (the oracle's numpy restatement of the reference
+per-row loop on a bounded row sample, rank 0, N=1) with its parity check, grm / reml
+(configs[1]: agmat GRM on 2,000 x 20,000, GFLOP/s dense-equivalent 2n^2m, and the 2-GRM REML),
+the split rehearsal, the covariate design, the end-to-end remma_epiAA call, the effect screen
+and the configs[4] leg.
 """
 import argparse
 import json
@@ -183,6 +189,22 @@ def exhaustive_live(plan, rows, p_cut, lib):
         parts.append(plan.scan("AA", rows[k:k + 2000], p_cut, n_slice=N.GMAT_SCREEN_NONE))
         log("exhaustive: %d / %d rows, %.0f s" % (min(k + 2000, rows.size), rows.size, time.perf_counter() - t0))
     return tuple(np.concatenate([p[t] for p in parts]) for t in range(6)), time.perf_counter() - t0
+
+
+DUMP_MAX_HITS = 64 * 1000 * 1000 // (6 * 8)  # --dump-outputs: six float64 arrays, 64 MB in all
+
+
+def dump_outputs(out_dir, hits):
+    """The timed path's result, as its caller receives it from the last timed step: the hit tuple
+    (i, j, eff, var, chi, p) merged over the ranks and sorted by (i, j), one float64 .npy per array
+    (the indices are exact in float64; a configs[2] step has about 11,000 hits, under 1 MB in all).
+    Above DUMP_MAX_HITS hits (64 MB in all) a fixed, seeded sample of the hits is written, in order."""
+    os.makedirs(out_dir, exist_ok=True)
+    keep = slice(None)
+    if hits[0].size > DUMP_MAX_HITS:
+        keep = np.sort(np.random.default_rng(0).choice(hits[0].size, DUMP_MAX_HITS, replace=False))
+    for name, a in zip(("i", "j", "eff", "var", "chi", "p"), hits):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[keep], dtype=np.float64))
 
 
 def grm_bench(n, m_grm, seed, reps=5):
@@ -595,6 +617,13 @@ def main():
     ap.add_argument("--n-snp", type=int, default=50000)
     ap.add_argument("--p-cut", type=float, default=1e-5)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the timed steps (full-triangle check, CPU baseline and parity, "
+                         "configs[1] GRM / REML, split rehearsal, covariates, end to end, effect screen, configs[4]); "
+                         "the --no-* switches below take legs out of a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's merged hits as DIR/<name>.npy (float64: i, j, eff, var, "
+                         "chi, p, sorted by (i, j))")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-grm", action="store_true")
@@ -622,6 +651,13 @@ def main():
                     help="launcher / process-group check only: every rank joins the group, exchanges its rank and "
                          "exits (no GPU work)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full_triangle and not args.full:
+        ap.error("--full-triangle recomputes the reference of the full-triangle check, a leg of --full")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_cpu = args.no_grm = args.no_eff = args.no_reml = args.no_e2e = args.no_cov = True
+        args.no_split = args.no_cfg5 = True
     # --gpus N without a launcher: start N ranks of this script now, before anything in this process
     # touches the GPU (gmat_amd.launch), and exit with their status; a WORLD_SIZE that contradicts
     # --gpus is an error
@@ -810,14 +846,17 @@ def main():
                     "traffic": None, "kernel": "screen level %d" % n_slice, "avg_launch_ms": avg_launch_s * 1e3,
                     "issued_ops_per_launch": ops / max(launches, 1)}
 
-    # full-triangle check: the last step's hits merged over the ranks against the exhaustive scan
-    merged = dist.gather_hits(res)
+    # the last step's hits merged over the ranks (sorted by (i, j)): what --dump-outputs and --hits-out
+    # write and the full-triangle check of --full compares against the exhaustive scan
+    merged = dist.gather_hits(res) if args.full or args.dump_outputs or args.hits_out else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, merged)
     live, t_live = None, None
     if args.full_triangle:
         ex_local, t_live = exhaustive_live(plan, rows, args.p_cut, lib)
         live = dist.gather_hits(ex_local)
         t_live = dist.allreduce_max(t_live)
-    full_tri = full_triangle_check(g, pvp, py, merged, args.p_cut, live) if rank == 0 else None
+    full_tri = full_triangle_check(g, pvp, py, merged, args.p_cut, live) if rank == 0 and args.full else None
     if rank == 0 and args.hits_out:
         np.savez(args.hits_out, i=merged[0], j=merged[1], eff=merged[2], var=merged[3], chi=merged[4], p=merged[5])
     if rank == 0 and t_live is not None:

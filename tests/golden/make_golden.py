@@ -176,9 +176,23 @@ def tiny(gmat, work, out):
     remma_epiAD(pheno, bed, [a, a * a], var, p_cut=1.0, out_file=os.path.join(out, "epiAD_all"))
     for name in ("epiAA_all", "epiDD_all", "epiAD_all"):
         path = os.path.join(out, name)
-        with open(path, "rb") as fi, gzip.open(path + ".gz", "wb", compresslevel=9) as fo:
-            fo.write(fi.read())
+        _gzip_in_parts(path)
         os.remove(path)
+
+
+GZ_PART_LINES = 30000  # lines of a result file per .gz part: every fixture file stays under 1 MiB
+
+
+def _gzip_in_parts(path):
+    """path -> path.gz, or path.part0.gz, path.part1.gz, ... (whole lines, in order) when the file has
+    more than GZ_PART_LINES lines; the tests read the parts back as one file."""
+    with open(path, "rb") as fi:
+        lines = fi.read().splitlines(keepends=True)
+    chunks = [lines[k:k + GZ_PART_LINES] for k in range(0, len(lines), GZ_PART_LINES)]
+    for k, chunk in enumerate(chunks):
+        name = path + (".gz" if len(chunks) == 1 else ".part%d.gz" % k)
+        with open(name, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", compresslevel=9, mtime=0) as fo:
+            fo.write(b"".join(chunk))
 
 
 def singles(gmat, work, out_mouse, out_tiny):

@@ -110,7 +110,7 @@ def test_bench_gpus2_sharded_full_cohort_identical(tmp_path):
     gloo) each scan part k of the reference's folded split (remma_epiAA.py:109-161) and rank 0 merges
     the hits.  The merged (i, j, eff, var, chi, p) tuples are byte-identical to the one-rank step's,
     and both equal the exhaustive (unscreened) full-triangle hit set (parity.full_triangle)."""
-    common = ["--steps", "1", "--warmup", "1", "--no-cpu", "--no-grm", "--no-eff", "--no-e2e", "--no-cov",
+    common = ["--full", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-grm", "--no-eff", "--no-e2e", "--no-cov",
               "--no-split", "--no-cfg5"]
     res, hits = {}, {}
     for g in (1, 2):

@@ -2,6 +2,7 @@
 
 These run without a GPU.  They make the oracle a trustworthy checker for the HIP path.
 """
+import glob
 import gzip
 import hashlib
 import io
@@ -18,9 +19,14 @@ TINY = os.path.join(os.path.dirname(__file__), "golden", "tiny")
 
 
 def _load_hits(path):
-    opener = gzip.open if path.endswith(".gz") else open
-    with opener(path, "rt") as f:
-        lines = f.read().splitlines()
+    # a golden <name>.gz may be stored as <name>.part0.gz, <name>.part1.gz, ... (whole lines, in order)
+    parts = [path] if os.path.exists(path) or not path.endswith(".gz") else sorted(glob.glob(path[:-3] + ".part*.gz"))
+    assert parts, path
+    lines = []
+    for part in parts:
+        opener = gzip.open if part.endswith(".gz") else open
+        with opener(part, "rt") as f:
+            lines += f.read().splitlines()
     if len(lines) <= 1:
         return lines[0], np.zeros((0, 5))
     return lines[0], np.loadtxt(io.StringIO("\n".join(lines[1:])), ndmin=2)

@@ -8,7 +8,7 @@ mkdir -p $OUT
 for spec in "$@"; do
   envs=""; [ "$spec" != base ] && envs=$(echo "$spec" | tr ',' ' ')
   f=$(echo "$spec" | tr -c 'A-Za-z0-9_\n' '_')
-  env $envs timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu --no-grm --no-eff --no-e2e --no-cov --no-cfg5 > $OUT/s_$f.json 2> $OUT/s_$f.log || { tail -20 $OUT/s_$f.log; exit 1; }
+  env $envs timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-cpu --no-grm --no-eff --no-e2e --no-cov --no-cfg5 > $OUT/s_$f.json 2> $OUT/s_$f.log || { tail -20 $OUT/s_$f.log; exit 1; }
   python -c "
 import json
 d = json.load(open('$OUT/s_$f.json'))

@@ -613,3 +613,21 @@ extern "C" int gmat_snp_test(gmat_geno *g, int kind, const double *pvp, const do
   GMAT_HIP(hipMemcpy(xpx, o2.p, m * sizeof(double), hipMemcpyDeviceToHost));
   return GMAT_OK;
 }
+
+// The coding rows of gmat_snp_test for the SNPs [j0, j0 + nc) of the panel, queued on s: x (nc x n fp64,
+// .fam order) = eff_x_kernel's additive (dom 0) or dominance (dom 1) coding minus centre[j0 + r]
+// (device, m values).  snp_test_chunk: the SNPs gmat_snp_test takes per pass.  (gmat_lmm_snp_test, lmm.hip)
+namespace gmat {
+int snp_coding_rows(hipStream_t s, const gmat_geno *g, int64_t j0, int64_t nc, const double *centre, int dom,
+                    double *x) {
+  if (nc <= 0) return GMAT_OK;
+  GMAT_CHECK(g && centre && x && j0 >= 0 && j0 + nc <= g->m, GMAT_E_ARG, "snp_coding_rows: bad arguments");
+  hipLaunchKernelGGL(eff_x_kernel, dim3((unsigned)nc), dim3(256), 0, s, g->packed.as<uint8_t>() + j0 * g->nb, g->nb, g->n,
+                     centre + j0, dom, x);
+  GMAT_HIP(hipGetLastError());
+  return GMAT_OK;
+}
+int64_t snp_test_chunk(int64_t n, int64_t m) {
+  return std::max<int64_t>(64, std::min<int64_t>(m, (int64_t)(1ll << 26) / std::max<int64_t>(n, 1)));
+}
+}  // namespace gmat

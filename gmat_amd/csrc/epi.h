@@ -987,6 +987,13 @@ struct gmat_epi {
     unsigned ltag[3] = {0, 0, 0};               // the live-block entries' tag of each set's last launch
     void *lm_ptr[3] = {nullptr, nullptr, nullptr};  // the entry buffer that tag refers to
   } lrc;  // compacted low-rank scan buffers (scan_lowrank)
+  // fixed-effect (conditional) epiAA test, gmat_lmm_epi_rows (lmm.hip), built by its first call: S = the
+  // centred additive codes in fp64 [m][n_pad] (storage order, zero padding), Y = S P, W = S o Y,
+  // d[i] = a_i'Pa_i, q[i] = a_i'Py
+  struct LmmState {
+    bool ready = false;
+    DBuf S, Y, W, d, q;
+  } lmm;
   ~gmat_epi() {
     gmat::epi::seg_free(seg);
     for (auto ev : kev) (void)hipEventDestroy(ev);

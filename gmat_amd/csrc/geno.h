@@ -27,3 +27,12 @@ struct gmat_geno {
 // heterozygote rows, the per-SNP counts): the sub-panels of a segmented scan plan (epi_seg.hip).  The
 // packed .bed rows are not copied (the scans never read them).
 int geno_subset(const gmat_geno *g, const int64_t *lo, const int64_t *hi, int nr, gmat_geno **out);
+
+namespace gmat {
+// fp64 coding rows of the single-SNP tests (eff.hip): x (nc x n, .fam order) for the SNPs [j0, j0 + nc),
+// additive (dom 0) or dominance (dom 1) coding minus centre[j0 + r] (device, m values), queued on s;
+// snp_test_chunk: the SNPs gmat_snp_test takes per pass
+int snp_coding_rows(hipStream_t s, const gmat_geno *g, int64_t j0, int64_t nc, const double *centre, int dom,
+                    double *x);
+int64_t snp_test_chunk(int64_t n, int64_t m);
+}  // namespace gmat

@@ -206,6 +206,32 @@ int gmat_append_hit_rows(const char *path, int64_t n, const int64_t *i, const in
  * products of remma_add.py:58-59 / remma_dom.py:60-61; the scaling by var_com and the
  * chi2 test stay on the host. */
 int gmat_snp_test(gmat_geno *g, int kind, const double *pvp, const double *py, double *xpy, double *xpx);
+/* ---- fixed-effect tests (uvlmm_gwas_add / _dom / _epiAA, uvlmm_gwas.py:12-198) ----
+ * The tested column e enters the model as a fixed covariate beside conditioning columns C (add: none;
+ * dom: the SNP's additive coding; epiAA: both SNPs' additive codings) and the other fixed effects, which
+ * P (p, n x n, .fam order; py = Py) has projected out.  With M = C'PC, c = C'Pe, r = C'Py:
+ * den = e'Pe - c'M^-1 c, num = e'Py - c'M^-1 r; eff = num/den (the reference's snp_eff), var = 1/den
+ * (snp_var), chi = num^2/den.  NaN in every output where the test is ill-posed: den <= 1e-10 e'Pe,
+ * det M <= 1e-10 M11 M22 (epiAA) or a zero pivot a'Pa (a monomorphic SNP).  Replaces the reference's
+ * dense solve per SNP / pair.  A number does not depend on chunk / block or on the rows of the call.
+ *
+ * Every SNP of the (imputed) panel; mode GMAT_GRM_ADD (e = g - 2f) or GMAT_GRM_DOM (C = [g - 2f],
+ * e = [g != 2] g - 2f(1-f)); chunk = SNPs per pass (0: as gmat_snp_test); eff, var, chi: n_snp values. */
+int gmat_lmm_snp_test(gmat_geno *g, int mode, const double *p, const double *py, int64_t chunk, double *eff,
+                      double *var, double *chi);
+/* epiAA (C = [a_i, a_j], e = a_i o a_j) for every pair (i, j > i) of the first SNPs `rows` (strictly
+ * increasing, < n_snp - 1): row i's pairs j = i+1 .. n_snp-1 contiguously, rows in list order; each
+ * output holds sum_i (n_snp - 1 - i) values, p = chi2.sf(chi, 1).  block = rows per pass (0: 256; at most
+ * 65,535).  e'Py and e'Pe come from the plan's exact pair evaluation (as gmat_epi_pairs).  The first call
+ * on a plan builds three m x n_pad fp64 matrices kept by the plan (GMAT_E_NOMEM when they do not fit);
+ * plans cut into SNP segments are refused. */
+int gmat_lmm_epi_rows(gmat_epi *e, const int64_t *rows, int64_t n_rows, int64_t block, double *eff, double *var,
+                      double *chi, double *p);
+/* last gmat_lmm_epi_rows on this process: [0] pairs, [1] seconds of the plan's one-off setup (0 when it
+ * was there), [2] seconds of the exact pair evaluation, [3] of the three dgemms, [4] of the combine
+ * kernel (HIP events), [5] total seconds */
+int gmat_lmm_stats(double *out8);
+
 /* Decoded fp64 dosage (m x n, SNP-major, .fam order; (c^2+c)/6: missing = 1/3) -- the
  * reference's read_plink_bed (_read_plink_bed.c:5-51). */
 int gmat_geno_decode(const gmat_geno *g, double *marker_mat);

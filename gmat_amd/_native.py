@@ -66,6 +66,9 @@ _PROTOS = {
     "gmat_lmm_stats": (_INT, [_P]),
     "gmat_probe_mx_accum":(_INT, [_INT, _P, _P, _P]),
     "gmat_probe_eig_bottom": (_INT, [_I64, _P, _INT, _D, _INT, _P, _P, _P, _P]),
+    "gmat_probe_dgemm": (_INT, [_I64, _I64, _I64, _D, _D, _INT, _P, _INT, _INT, _I64, _P, _INT, _INT, _I64, _P, _I64]),
+    "gmat_probe_cholesky": (_INT, [_I64, _P, _I64, _INT, _P, _P, _P, _P, _P, _P]),
+    "gmat_probe_dot_rows": (_INT, [_I64, _I64, _P, _I64, _P, _I64, _P]),
     "gmat_comm_unique_id": (_INT, [_P]),
     "gmat_comm_init": (_INT, [_P, _INT, _INT, _P]),
     "gmat_comm_destroy": (_INT, [_P]),

@@ -133,7 +133,7 @@ __device__ __forceinline__ bool factor_invert_block(double (*Ls)[NB + 1], double
         r[q] = Ls[lane][c0 + q];
         dr[q] = Ls[c0 + li][c0 + q];
       }
-      double pv = 1.0, ipv = 1.0;
+      double pd = 1.0, ipv = 1.0;  // this lane's pivot (j = li) and its 1 / sqrt
 #pragma unroll
       for (int j = 0; j < PW; ++j) {
         double d = bcast16(dr[j], j);
@@ -146,7 +146,7 @@ __device__ __forceinline__ bool factor_invert_block(double (*Ls)[NB + 1], double
         inv = inv * fma(-0.5 * d * inv, inv, 1.5);
         inv = inv * fma(-0.5 * d * inv, inv, 1.5);
         if (li == j) {
-          pv = d * inv;
+          pd = d;
           ipv = inv;
         }
         dr[j] *= inv;
@@ -158,10 +158,16 @@ __device__ __forceinline__ bool factor_invert_block(double (*Ls)[NB + 1], double
           r[k] = fma(-r[j], t, r[k]);
         }
       }
+      // L_jj = d / sqrt(d) with one residual correction: correctly rounded, like a library sqrt (d * inv
+      // alone is off by up to ~1.2 ulp, which at n = 1 is all of |L L' - A|).  Once per panel, after the
+      // pivot chain: the columns were scaled by inv.
+      const double pg = pd * ipv;
+      const double pv = fma(fma(-pg, pg, pd), 0.5 * ipv, pg);
       if (lane >= c0)
 #pragma unroll
         for (int q = 0; q < PW; ++q) Ls[lane][c0 + q] = (c0 + q <= lane) ? r[q] : 0.0;
       if (lane < PW) {
+        Ls[c0 + lane][c0 + lane] = pv;  // over r's d * inv (same wave: LDS writes in program order); a failed pivot 1
         piv[c0 + lane] = (c0 + lane < kb) ? pv : 1.0;
         ipiv[c0 + lane] = ipv;
       }

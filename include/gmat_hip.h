@@ -272,6 +272,27 @@ int gmat_probe_mx_accum(int n_steps, const uint8_t *codes, const uint8_t *scales
  * residual norms) and iters_out may be NULL.  Test support. */
 int gmat_probe_eig_bottom(int64_t n, const double *a_host, int ne, double tol, int maxit, double *w_out,
                           double *z_out, double *res_out, int *iters_out);
+/* The dense fp64 layer (csrc/dla.h) on host arrays, on the null stream.  Test support: whole host
+ * buffers are uploaded, padding included, and whole output buffers are downloaded.
+ * c[M x ldc] = alpha op(a)[M x K] op(b)[K x N] + beta c.  a is stored M x lda (K x lda when trans_a), b
+ * K x ldb (N x ldb when trans_b); a_i8 / b_i8: that operand holds int8 (both: GMAT_E_ARG; no mask then).
+ * mask: 0 every tile, 1 the 64 x 64 tiles with tile_row >= tile_col, 2 as 1 with the k loop started at
+ * the tile's first row (the other tiles of c are unspecified). */
+int gmat_probe_dgemm(int64_t M, int64_t N, int64_t K, double alpha, double beta, int mask, const void *a,
+                     int a_i8, int trans_a, int64_t lda, const void *b, int b_i8, int trans_b, int64_t ldb,
+                     double *c, int64_t ldc);
+/* The blocked Cholesky of a (n x lda, lower triangle read).  mode 0: cholesky(); 1: cholesky_inverse()
+ * without vinv; 2: with vinv; 3: cholesky(), chol_lower_inverse() into linv and spd_inverse_from_chol()
+ * into vinv.  a_out (n x lda): a after the call (L in its lower triangle in modes 0 and 3, scratch
+ * otherwise); dinv (n x 64): the diagonal blocks' inverses; linv, vinv (n x n; may be NULL when the mode
+ * does not produce them).  Outputs start as NaN on the device.  A non-positive pivot is not an error
+ * here: GMAT_OK with *info > 0. */
+int gmat_probe_cholesky(int64_t n, const double *a, int64_t lda, int mode, double *a_out, double *dinv,
+                        double *linv, double *vinv, double *logdet, int *info);
+/* out[r] = sum_k a[r, k] b[r, k] for r < rows, k < n.  b NULL: a vector of ones; ldb 0: one row of n
+ * shared by every r. */
+int gmat_probe_dot_rows(int64_t rows, int64_t n, const double *a, int64_t lda, const double *b, int64_t ldb,
+                        double *out);
 
 #ifdef __cplusplus
 }

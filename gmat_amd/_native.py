@@ -48,6 +48,7 @@ _PROTOS = {
     "gmat_epi_pairs": (_INT, [_P, _INT, _P, _I64, _P, _P, _P, _P]),
     "gmat_epi_stats": (_INT, [_P, _P]),
     "gmat_epi_audit": (_INT, [_P, _INT, _P, _I64, _P]),
+    "gmat_epi_pair_audit": (_INT, [_P, _INT, _P, _I64, _P]),
     "gmat_epi_kernel_stats": (_INT, [_P, _P]),
     "gmat_epi_kernel_stats_ext": (_INT, [_P, _P, _INT, _P]),
     "gmat_epi_info": (_INT, [_P, _P]),

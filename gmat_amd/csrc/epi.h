@@ -670,6 +670,7 @@ struct PairArgs {
   unsigned long long *counter;
   int64_t *oi, *oj;  // surviving pairs
   double *mpart;     // pair_mxr_kernel with segments: w'P~w per (segment, pair), added by pair_test_kernel
+  double *audit;     // gmat_epi_pair_audit: [2][np] var_lo, eff_hi instead of the survivor list (else null)
 };
 
 // the pair screen's test of pair p given M = w'P~w: kept unless its p-value is certainly >= p_cut
@@ -677,6 +678,11 @@ __device__ __forceinline__ void pair_test(const PairArgs &x, int64_t p, double M
   const double var = M + x.side[p], sw = x.side[4 * x.np + p];
   const double var_lo = var - x.rho * sw - x.side[x.np + p] - 1e-12 * fabs(M);
   const double eff_hi = fabs(x.side[2 * x.np + p]) + x.side[3 * x.np + p];
+  if (x.audit) {
+    x.audit[p] = var_lo;
+    x.audit[x.np + p] = eff_hi;
+    return;
+  }
   if (!(var_lo > 0.0) || eff_hi * eff_hi * (1.0 + 1e-9) >= x.chi_cut * var_lo) {
     const unsigned long long k = atomicAdd(x.counter, 1ULL);
     x.oi[k] = x.ci[p];
@@ -684,12 +690,17 @@ __device__ __forceinline__ void pair_test(const PairArgs &x, int64_t p, double M
   }
 }
 
-// One wave per pair, PS_PPW pairs per wave; z, diag(P) and Py staged once per workgroup in LDS as
-// fp32.  The sums run in fp32 with a certified slack: each lane adds its n_pad / 64 terms per
-// quantity and the wave reduces the lane partials in fp64; the inputs' fp32 rounding (U = P x
-// codes, z, diag(P), Py: 2^-24 relative each) adds a few 2^-24 per term (the bound is below; it is
-// carried to the pair screen's variance bound, side[np + p], and to its eff bound, side[3 np + p]).
+// One wave per pair; a wave owns PS_PPW consecutive candidates and takes up to PS_G neighbours with
+// the same first SNP together: the i side (a_i, U16_a[i]) is read and converted once per group and
+// everything that depends on i alone (pair_side_kernel's g terms) is formed once per chunk of 8
+// individuals, in registers that live for that chunk only.  The low-rank screen emits one first SNP's
+// candidates next to each other, so most groups are full; a list in any order runs as groups of one.
+// z, diag(P) and Py are staged once per workgroup in LDS as fp32.  The sums run in fp32 with a
+// certified slack: each lane adds its n_pad / 64 terms per quantity and the wave reduces the lane
+// partials in fp64 (the bound is next to the code; it is carried to the pair screen's variance bound,
+// side[np + p], and to its eff bound, side[3 np + p]).  A pair's numbers do not depend on its group.
 constexpr int PS_PPW = 8;
+constexpr int PS_G = 2;  // pairs to a group, 1 .. 4 (measured: DESIGN.md 6; the registers of 3 and 4 cost a wave per SIMD)
 
 
 // The same quadratic form with each pair's w held in REGISTERS (n_pad <= 128 PXR_NK): a wave owns 32
@@ -1180,7 +1191,8 @@ int refine(gmat_epi *e, hipStream_t st, const Coding &L, const Coding &R, const 
 bool pair_screen_fits(const gmat_epi *e);
 int default_lr_rank(const gmat_epi *e);
 int pair_screen(gmat_epi *e, hipStream_t st, const Coding &L, const Coding &R, const int8_t *slp, const int8_t *srp,
-                const int64_t *pi, const int64_t *pj, int64_t np, double chi_cut, int64_t *n_out, bool reset = true);
+                const int64_t *pi, const int64_t *pj, int64_t np, double chi_cut, int64_t *n_out, bool reset = true,
+                double *audit = nullptr);
 // plan creation (epi_plan.hip): a plan of one panel (state: another plan's spectral state, or null)
 // (allow_seg false: a plan of this one panel even when seg_snps() would cut it -- the segments' sub-plans)
 int epi_create_impl(gmat_epi **out, gmat_geno *g, const double *pvp, const double *py, int n_slice,

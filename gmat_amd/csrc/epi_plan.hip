@@ -312,16 +312,19 @@ int default_lr_rank(const gmat_epi *e) { return pair_screen_fits(e) && !getenv("
 // Survivors are appended to cand2 at counter2: `reset` zeroes the counter first, `n_out` (when given)
 // receives its value after a stream synchronisation; without it the call only enqueues (the scan
 // screens candidate ranges in chunks beside the later launches and reads the total at flush time).
+// With `audit` ([2][np], gmat_epi_pair_audit) the same launches store every pair's var_lo and eff_hi
+// there and leave the survivor list and its counter alone; the side terms stay in e->ps_side.
 int pair_screen(gmat_epi *e, hipStream_t st, const Coding &L, const Coding &R, const int8_t *slp, const int8_t *srp,
-                const int64_t *pi, const int64_t *pj, int64_t np, double chi_cut, int64_t *n_out, bool reset) {
+                const int64_t *pi, const int64_t *pj, int64_t np, double chi_cut, int64_t *n_out, bool reset,
+                double *audit) {
   if (n_out) *n_out = 0;
   if (np <= 0 && !n_out) return GMAT_OK;
   if (np <= 0 && reset) return GMAT_OK;
   const int nK = e->nK;
   GMAT_CHECK(nK <= 63, GMAT_E_ARG, "pair screen: %d stages (at most 63: pair_mxw_kernel's squares)", nK);
   GMAT_CHECK(L.U16.p && R.U16.p && L.nibI.p && R.nibJ.p && e->mx_tiles.p && e->z.p && e->dg.p && e->py.p && L.qa.p &&
-                 R.qb.p && e->cand2_i.p && e->cand2_j.p && e->counter2.p &&
-                 e->cand2_i.bytes >= (size_t)np * 8 && L.U16.bytes >= (size_t)e->m * e->n_pad * 2 &&
+                 R.qb.p && (audit || (e->cand2_i.p && e->cand2_j.p && e->counter2.p &&
+                 e->cand2_i.bytes >= (size_t)np * 8)) && L.U16.bytes >= (size_t)e->m * e->n_pad * 2 &&
                  R.U16.bytes >= (size_t)e->m * e->n_pad * 2 && e->mx_tiles.bytes >= (size_t)nK * nK * MX_TILE,
              GMAT_E_ARG, "pair screen: plan buffers missing (U16 %d %d nib %d %d mx %zu z %d cand2 %zu / %lld counter2 %d)",
              L.U16.p != nullptr, R.U16.p != nullptr, L.nibI.p != nullptr, R.nibJ.p != nullptr, e->mx_tiles.bytes,
@@ -362,7 +365,24 @@ int pair_screen(gmat_epi *e, hipStream_t st, const Coding &L, const Coding &R, c
   x.counter = e->counter2.as<unsigned long long>();
   x.oi = e->cand2_i.as<int64_t>();
   x.oj = e->cand2_j.as<int64_t>();
-  if (reset) GMAT_HIP(hipMemsetAsync(e->counter2.p, 0, 8, st));
+  x.audit = audit;
+  if (reset && !audit) GMAT_HIP(hipMemsetAsync(e->counter2.p, 0, 8, st));
+  if (np > 0 && !audit && getenv("GMAT_DEBUG")) {
+    // how far pair_side_kernel can share the i side: runs of one first SNP inside the 32-candidate
+    // blocks of a workgroup, and the groups its waves form (PS_PPW candidates, at most PS_G a group)
+    std::vector<int64_t> hc(np);
+    GMAT_HIP(hipStreamSynchronize(st));
+    GMAT_HIP(hipMemcpy(hc.data(), pi, np * 8, hipMemcpyDeviceToHost));
+    int64_t runs = 0, groups = 0;
+    for (int64_t t = 0, g = 0; t < np; ++t) {
+      const bool same = t > 0 && hc[t] == hc[t - 1];
+      if (!same || t % 32 == 0) ++runs;
+      g = (same && t % PS_PPW != 0 && g < PS_G) ? g + 1 : 1;
+      if (g == 1) ++groups;
+    }
+    fprintf(stderr, "pair screen: %lld candidates, %lld runs in blocks of 32 (mean %.2f), %lld groups (mean %.2f)\n",
+            (long long)np, (long long)runs, (double)np / runs, (long long)groups, (double)np / groups);
+  }
   if (np > 0) {
   static bool attr = false;
   if (!attr) {
@@ -411,7 +431,7 @@ int pair_screen(gmat_epi *e, hipStream_t st, const Coding &L, const Coding &R, c
   GMAT_HIP(hipGetLastError());
   GMAT_TRY(kt_end(e, st, KT_PAIR_MX, kt0, (double)np));
   }
-  if (!n_out) return GMAT_OK;
+  if (!n_out || audit) return GMAT_OK;
   GMAT_HIP(hipMemcpyAsync(e->pins.count2.p, e->counter2.p, 8, hipMemcpyDeviceToHost, st));
   GMAT_HIP(hipStreamSynchronize(st));
   *n_out = (int64_t)*e->pins.count2.as<unsigned long long>();
@@ -1165,5 +1185,49 @@ extern "C" int gmat_epi_audit(gmat_epi *e, int kind, const int64_t *pairs, int64
   GMAT_HIP(hipGetLastError());
   GMAT_HIP(hipMemcpyAsync(out5, dout.p, n_pairs * 5 * 8, hipMemcpyDeviceToHost, e->s));
   GMAT_HIP(hipStreamSynchronize(e->s));
+  return GMAT_OK;
+}
+
+// ------------------------------------------------------------------ pair-screen audit (diagnostic)
+// The pair screen's own numbers for listed pairs, in the listed order: pair_side_kernel and the w'P~w
+// kernel run on the list as they do on a screen's candidates, and pair_test's quantities are returned
+// instead of a survivor list: out[7 t + ..] = {side, side_slack, eff, eff_slack, sum w^2, var_lo, eff_hi}.
+// The caller compares them with the exact refine (gmat_epi_pairs): var >= var_lo and |eff| <= eff_hi
+// must hold for every pair (NaN or -inf in var_lo: the screen keeps the pair).
+extern "C" int gmat_epi_pair_audit(gmat_epi *e, int kind, const int64_t *pairs, int64_t n_pairs, double *out7) {
+  GMAT_CHECK(e && (n_pairs == 0 || (pairs && out7)), GMAT_E_ARG, "gmat_epi_pair_audit: bad arguments");
+  GMAT_CHECK(kind >= 0 && kind <= 2, GMAT_E_ARG, "gmat_epi_pair_audit: bad kind");
+  if (n_pairs == 0) return GMAT_OK;
+  GMAT_CHECK(!e->seg, GMAT_E_ARG, "gmat_epi_pair_audit: not available for a plan split into individual segments");
+  GMAT_CHECK(pair_screen_fits(e), GMAT_E_ARG, "gmat_epi_pair_audit: the pair screen does not run at %d stages", e->nK);
+  int lc, rc;
+  kind_codings(kind, &lc, &rc);
+  GMAT_TRY(build_coding(e, lc));
+  GMAT_TRY(build_coding(e, rc));
+  std::vector<int64_t> hi(n_pairs), hj(n_pairs);
+  for (int64_t t = 0; t < n_pairs; ++t) {
+    hi[t] = pairs[2 * t];
+    hj[t] = pairs[2 * t + 1];
+    GMAT_CHECK(hi[t] >= 0 && hi[t] < e->m && hj[t] >= 0 && hj[t] < e->m, GMAT_E_ARG, "pair %lld out of range",
+               (long long)t);
+  }
+  DBuf di, dj, da;
+  GMAT_TRY(di.alloc(n_pairs * 8));
+  GMAT_TRY(dj.alloc(n_pairs * 8));
+  GMAT_TRY(da.alloc(n_pairs * 2 * 8));
+  GMAT_HIP(hipMemcpy(di.p, hi.data(), n_pairs * 8, hipMemcpyHostToDevice));
+  GMAT_HIP(hipMemcpy(dj.p, hj.data(), n_pairs * 8, hipMemcpyHostToDevice));
+  // chi_cut does not enter the returned quantities
+  GMAT_TRY(pair_screen(e, e->s, e->code[lc], e->code[rc], screen_panel(e, lc), screen_panel(e, rc), di.as<int64_t>(),
+                       dj.as<int64_t>(), n_pairs, 1.0, nullptr, false, da.as<double>()));
+  std::vector<double> side((size_t)5 * n_pairs), au((size_t)2 * n_pairs);
+  GMAT_HIP(hipMemcpyAsync(side.data(), e->ps_side.p, side.size() * 8, hipMemcpyDeviceToHost, e->s));
+  GMAT_HIP(hipMemcpyAsync(au.data(), da.p, au.size() * 8, hipMemcpyDeviceToHost, e->s));
+  GMAT_HIP(hipStreamSynchronize(e->s));
+  for (int64_t t = 0; t < n_pairs; ++t) {
+    for (int k = 0; k < 5; ++k) out7[7 * t + k] = side[(size_t)k * n_pairs + t];
+    out7[7 * t + 5] = au[t];
+    out7[7 * t + 6] = au[n_pairs + t];
+  }
   return GMAT_OK;
 }

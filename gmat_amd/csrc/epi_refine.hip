@@ -561,6 +561,201 @@ __global__ __launch_bounds__(256) void refine8_fin_kernel(int64_t np, const doub
   pv[p] = (cc < 0.0) ? 1.0 : erfc(sqrt(0.5 * cc));
 }
 
+// The wave's sum of a lane value, the butterfly over lane ^ 1, 2, 4, ..., 32 in fp32 (every lane ends
+// with the sum), without LDS: the first four steps are DPP operands inside a row of 16 lanes (after
+// the quad steps a quad's lanes hold one value, so the mirrored half row and row stand in for
+// lane ^ 4 and lane ^ 8), the last two swap rows and halves (v_permlane16_swap, v_permlane32_swap).
+// (__shfl_xor on doubles is two ds_bpermute per step: about 50 LDS round trips per pair, one after
+// the other; the same butterfly in fp64 by DPP costs as many VALU cycles as the pair's main loop.)
+template <int CTRL>
+__device__ __forceinline__ float ps_dpp(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float ps_wave_sum(float r) {
+#pragma clang fp contract(off)
+  r = r + ps_dpp<0xB1>(r);   // quad_perm [1, 0, 3, 2]
+  r = r + ps_dpp<0x4E>(r);   // quad_perm [2, 3, 0, 1]
+  r = r + ps_dpp<0x141>(r);  // row_half_mirror
+  r = r + ps_dpp<0x140>(r);  // row_mirror
+  const auto h = __builtin_amdgcn_permlane16_swap(__float_as_uint(r), __float_as_uint(r), false, false);
+  r = __uint_as_float(h[0]) + __uint_as_float(h[1]);
+  const auto w = __builtin_amdgcn_permlane32_swap(__float_as_uint(r), __float_as_uint(r), false, false);
+  return __uint_as_float(w[0]) + __uint_as_float(w[1]);
+}
+
+// One group of pair_side_kernel: the G pairs (i, j_s), s < G, that stand at p0 .. p0 + G - 1 (lane k
+// of the wave holds cj[pw + k] in my_j; the group starts at lane k0).  With al = alpha_i, be = beta_j,
+// w = a o b, u = U16_a[i], v = U16_b[j] the sums of the O(n) terms are regrouped so that what depends
+// on i alone is formed once per individual and group:
+//   g1 = a (al z - u):            sum w (al be z - be u - al v) = be sum b g1 - al sum (b a) v
+//   g3 = diag(P) a^2:             sum diag(P) w^2 = sum b^2 g3
+//   g5 = (a - al) Py:             eff = sum b g5 - be sum g5
+//   g6 = a (|u| + |al| |z|), g5m = |g5| + 2^-23 |al Py|: the magnitudes that carry the slack
+// Per individual and pair that leaves two conversions (b, v), |v|, b a, b^2 and eleven FMAs, packed two
+// individuals to an instruction.  Contraction is
+// off and every FMA is written out: a pair's sums are the same instructions on the same operands in
+// every instantiation, so its five outputs do not depend on G or on its place in the group.
+template <int G>
+__device__ __forceinline__ void pair_side_group(const PairArgs &x, const float *zdp, int lane, int64_t p0, int64_t i,
+                                                int my_j, int k0) {
+#pragma clang fp contract(off)
+  typedef _Float16 h8_ __attribute__((ext_vector_type(8)));
+  const int64_t n_pad = x.n_pad;
+  const double dal = x.alpha[i];
+  const float al = (float)dal, aal = fabsf(al);
+  const int8_t *pa = x.a + i * n_pad;
+  const _Float16 *ua = x.Ua + i * n_pad;
+  int64_t j[G];
+  const int8_t *pb[G];
+  const _Float16 *ub[G];
+#pragma unroll
+  for (int s = 0; s < G; ++s) {
+    j[s] = __builtin_amdgcn_readfirstlane(__shfl(my_j, k0 + s));
+    pb[s] = x.b + j[s] * n_pad;
+    ub[s] = x.Ub + j[s] * n_pad;
+  }
+  // every sum as a pair of partial sums, of the lane's even and odd individuals: two individuals per
+  // packed fp32 instruction (the kernel is bound by VALU issue, a wave64 fp32 instruction holding its
+  // SIMD for four cycles, packed or not).  The screen codes are 0, 1, 2 (flip_panel_kernel; a plan
+  // takes no missing genotypes): they convert from unsigned bytes and are their own magnitudes.
+  const v2f_ z2 = {0.f, 0.f};
+  v2f_ sA[G], sAa[G], sB[G], sBa[G], s2[G], s2a[G], s3[G], s3a[G], sw[G], ef[G], efa[G];
+#pragma unroll
+  for (int s = 0; s < G; ++s) sA[s] = sAa[s] = sB[s] = sBa[s] = s2[s] = s2a[s] = s3[s] = s3a[s] = sw[s] = ef[s] = efa[s] = z2;
+  v2f_ g5s = z2, g5ms = z2;  // sum g5, sum g5m: of i alone
+  const v2f_ al2 = {al, al}, aal2 = {aal, aal}, tiny2 = {0x1p-23f, 0x1p-23f};
+  // The loads of a wave's next 512 individuals go out before the arithmetic of the present ones: a wave
+  // is one chain of gather latency and arithmetic, and only a few waves fit a SIMD, so what a wave
+  // does not overlap itself is mostly lost (the last iteration reloads its own lines: no branch).
+  struct Gathered {
+    v2i_ va, vb[G];
+    h8_ u8, v8[G];
+  };
+  auto gather = [&](int64_t q) __attribute__((always_inline)) {
+    Gathered d;
+    d.va = *(const v2i_ *)(pa + q);
+    d.u8 = *(const h8_ *)(ua + q);
+#pragma unroll
+    for (int s = 0; s < G; ++s) {
+      d.vb[s] = *(const v2i_ *)(pb[s] + q);
+      d.v8[s] = *(const h8_ *)(ub[s] + q);
+    }
+    return d;
+  };
+  Gathered nxt = gather(8 * lane < n_pad ? 8 * lane : 0);
+  for (int64_t q0 = 8 * lane; q0 < n_pad; q0 += 512) {
+    const Gathered cur = nxt;
+    nxt = gather(q0 + 512 < n_pad ? q0 + 512 : q0);
+    __builtin_amdgcn_sched_barrier(0);  // (the scheduler sinks the loads to their use otherwise)
+    const v2i_ va = cur.va;
+    const h8_ u8 = cur.u8;
+    const v2i_ *vb = cur.vb;
+    const h8_ *v8 = cur.v8;
+    const uint8_t *ca = (const uint8_t *)&va;
+    // z, diag(P), Py of the lane's 8 individuals as 16-byte LDS reads (a lane's 32 bytes: 8 scalar reads at
+    // a 32-byte lane stride were 8-way bank conflicts).  Lanes with bit 3 set read their second half
+    // first: each 16-lane group of a ds_read_b128 then covers all 64 banks (in one order the groups'
+    // lanes l and l + 8 or l + 24 met on a bank, 2-way: ~40 % of the kernel's cycles by SQ_LDS_BANK_CONFLICT)
+    float zz8[8], dd8[8], yy8[8];
+    {
+      const int o1 = (lane & 8) ? 4 : 0, o2 = 4 - o1;
+      const bool swp = lane & 8;
+      auto rd2 = [&](const float *base, float *dst) __attribute__((always_inline)) {
+        const float4 f1 = *(const float4 *)&base[q0 + o1];
+        const float4 f2 = *(const float4 *)&base[q0 + o2];
+        *(float4 *)&dst[0] = swp ? f2 : f1;
+        *(float4 *)&dst[4] = swp ? f1 : f2;
+      };
+      rd2(zdp, zz8);
+      rd2(zdp + n_pad, dd8);
+      rd2(zdp + 2 * n_pad, yy8);
+    }
+#pragma unroll
+    for (int h = 0; h < 8; h += 2) {
+      const v2f_ av = {(float)ca[h], (float)ca[h + 1]}, uu = {(float)u8[h], (float)u8[h + 1]};
+      const v2f_ z = {zz8[h], zz8[h + 1]}, d = {dd8[h], dd8[h + 1]}, y = {yy8[h], yy8[h + 1]};
+      const v2f_ g1 = av * __builtin_elementwise_fma(al2, z, -uu);
+      const v2f_ g6 = av * __builtin_elementwise_fma(aal2, __builtin_elementwise_abs(z), __builtin_elementwise_abs(uu));
+      const v2f_ g3 = d * (av * av), ag3 = __builtin_elementwise_abs(g3);
+      const v2f_ g5 = (av - al2) * y;
+      const v2f_ g5m = __builtin_elementwise_fma(tiny2, __builtin_elementwise_abs(al2 * y), __builtin_elementwise_abs(g5));
+      g5s = g5s + g5;
+      g5ms = g5ms + g5m;
+#pragma unroll
+      for (int s = 0; s < G; ++s) {
+        const uint8_t *cb = (const uint8_t *)&vb[s];
+        const v2f_ bv = {(float)cb[h], (float)cb[h + 1]}, vv = {(float)v8[s][h], (float)v8[s][h + 1]};
+        const v2f_ avv = __builtin_elementwise_abs(vv);
+        const v2f_ ba = bv * av, b2 = bv * bv;  // exact small integers
+        sA[s] = __builtin_elementwise_fma(bv, g1, sA[s]);
+        sAa[s] = __builtin_elementwise_fma(bv, g6, sAa[s]);
+        sB[s] = __builtin_elementwise_fma(ba, vv, sB[s]);
+        sBa[s] = __builtin_elementwise_fma(ba, avv, sBa[s]);
+        s2[s] = __builtin_elementwise_fma(av, vv, s2[s]);
+        s2a[s] = __builtin_elementwise_fma(av, avv, s2a[s]);
+        s3[s] = __builtin_elementwise_fma(b2, g3, s3[s]);
+        s3a[s] = __builtin_elementwise_fma(b2, ag3, s3a[s]);
+        sw[s] = __builtin_elementwise_fma(ba, ba, sw[s]);
+        ef[s] = __builtin_elementwise_fma(bv, g5, ef[s]);
+        efa[s] = __builtin_elementwise_fma(bv, g5m, efa[s]);
+      }
+    }
+  }
+  // the wave's sums: lane s < G keeps pair s's (every lane holds them after the butterfly), so that the
+  // fp64 combinations below run once per group, not once per pair
+  auto wsum = [](v2f_ v) __attribute__((always_inline)) { return ps_wave_sum(v[0] + v[1]); };
+  auto pick = [&](const v2f_(&acc)[G]) __attribute__((always_inline)) {
+    float r = wsum(acc[0]);
+#pragma unroll
+    for (int s = 1; s < G; ++s) {
+      const float v = wsum(acc[s]);
+      r = lane == s ? v : r;
+    }
+    return (double)r;
+  };
+  const double G5 = (double)wsum(g5s), G5m = (double)wsum(g5ms);
+  // Rounding.  A lane adds m = n_pad / 64 terms per sum (m / 2 per parity and one more rounding to join
+  // the two), one fp32 rounding each, and the wave's butterfly adds six more (each of a partial sum, at
+  // most the magnitude sum); a term carries the roundings of its i-side factor: g1 within 5 x 2^-24 g6 of a (al z - u) (al, z to fp32, the FMA, the product;
+  // |g1| <= g6), g3 within 3 x 2^-24 |g3|, g5 within 4 x 2^-24 g5m of (a - al) Py (al to fp32 moves it by
+  // 2^-24 |al Py|, which g5m carries; the difference, Py, the product); b, b a, b^2, a and the fp16 values
+  // convert exactly.  So every sum is within (m + 12) 2^-24 of its true magnitude sum, and that within
+  // (m + 7) 2^-24, relative, of the computed one (sAa for sA, ...): fsl = 2 (m + 8) 2^-24 covers both for
+  // every m, with nearly half of it to spare at the bench's m = 32; the combinations below are fp64.
+  // sum w^2 is a sum of integers below 2^24: exact.  U is stored in fp16: a normal value is within 2^-11 of
+  // U, relative, so the U terms (su, their magnitudes from the rounded values) are within 2^-10.9 su; a
+  // subnormal one within 2^-25 absolute, at most 2^-25 (|alpha| + |beta|) 4 n_pad in total (an overflow
+  // gives inf / NaN: the pair is kept).  Plus the fp64 rounding of U = P x codes and of the host terms
+  // (far inside 1e-10 of the magnitudes).  side[3 np + p] is the eff bound's slack.
+  const double fsl = 2.0 * (double)(n_pad / 64 + 8) * 0x1p-24;
+  const double r[11] = {pick(sA), pick(sAa), pick(sB), pick(sBa), pick(s2), pick(s2a),
+                        pick(s3), pick(s3a), pick(sw), pick(ef), pick(efa)};
+  int64_t jl = j[0];
+#pragma unroll
+  for (int s = 1; s < G; ++s) jl = lane == s ? j[s] : jl;
+  if (lane < G) {
+    const int64_t p = p0 + lane;
+    const double dbe = x.beta[jl], dab = dal * dbe;
+    const double s1 = dbe * r[0] - dal * r[2], s1a = fabs(dbe) * r[1] + fabs(dal) * r[3];
+    const double t3 = dbe * dbe * x.qa[i], t5 = dal * dal * x.qb[jl], t7 = dab * dab * x.zz, t8 = 2.0 * dab * r[4],
+                 t4 = -2.0 * dab * dbe * x.ra[i], t6 = -2.0 * dab * dal * x.rb[jl];
+    x.side[p] = r[6] + 2.0 * s1 + t3 + t5 + t7 + t8 + t4 + t6;
+    const double su = 2.0 * s1a + 2.0 * fabs(dab) * r[5];
+    x.side[x.np + p] = fsl * (su + r[7]) + 0x1p-10 * su + 0x1p-23 * (fabs(dal) + fabs(dbe)) * 4.0 * (double)n_pad +
+                       1e-10 * (r[7] + su + fabs(t3) + fabs(t5) + fabs(t7) + fabs(t4) + fabs(t6));
+    x.side[2 * x.np + p] = r[9] - dbe * G5;
+    x.side[3 * x.np + p] = (fsl + 1e-10) * (r[10] + fabs(dbe) * G5m);
+    x.side[4 * x.np + p] = r[8];
+  }
+}
+
+// The O(n) terms of the pair screen.  Its bytes are gathered rows (a_i, U16_a[i], b_j, U16_b[j]: 6 n_pad
+// bytes per side, from tables far larger than the Infinity Cache), but neither they nor the arithmetic
+// set its time: with a fifth of the fabric bytes and a third of the VALU instructions gone (the i side
+// shared by a group, packed fp32) it ran as before.  Each wave is one chain -- gather, wait, arithmetic,
+// next 512 individuals, ..., reduction -- and three or four waves a SIMD do not cover each other's
+// waits; what shortened it is in pair_side_group: the next gathers issued before the arithmetic, a
+// reduction without LDS round trips, and half as many chains (DESIGN.md 6 has the measurements).
 __global__ __launch_bounds__(256) void pair_side_kernel(PairArgs x) {
   extern __shared__ __attribute__((aligned(16))) float zdp[];  // [3][n_pad]: z, diag(P), Py
   const int64_t n_pad = x.n_pad;
@@ -571,86 +766,27 @@ __global__ __launch_bounds__(256) void pair_side_kernel(PairArgs x) {
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int k = 0; k < PS_PPW; ++k) {
-    const int64_t p = ((int64_t)blockIdx.x * 4 + wv) * PS_PPW + k;
-    if (p >= x.np) return;
-    const int64_t i = x.ci[p], j = x.cj[p];
-    const double dal = x.alpha[i], dbe = x.beta[j], dab = dal * dbe;
-    const float al = (float)dal, be = (float)dbe, ab = (float)dab;
-    const int8_t *pa = x.a + i * n_pad, *pb = x.b + j * n_pad;
-    const _Float16 *ua = x.Ua + i * n_pad, *ub = x.Ub + j * n_pad;
-    float s1 = 0, s1a = 0, s2 = 0, s2a = 0, s3 = 0, s3a = 0, ef = 0, efa = 0, sw = 0;
-    // (the codes at 2 bits instead of int8, a quarter of the code bytes, measured the same: 18.3 ms per
-    // configs[2] step either way; the gathers are latency-bound)
-    for (int64_t q0 = 8 * lane; q0 < n_pad; q0 += 512) {
-      const v2i_ va = *(const v2i_ *)(pa + q0), vb = *(const v2i_ *)(pb + q0);
-      const int8_t *ca = (const int8_t *)&va, *cb = (const int8_t *)&vb;
-      typedef _Float16 h8_ __attribute__((ext_vector_type(8)));
-      const h8_ u8 = *(const h8_ *)(ua + q0), v8 = *(const h8_ *)(ub + q0);
-      float uu[8], vv[8];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        uu[t] = (float)u8[t];
-        vv[t] = (float)v8[t];
-      }
-      // z, diag(P), Py of the lane's 8 individuals as 16-byte LDS reads (a lane's 32 bytes: 8 scalar reads at
-      // a 32-byte lane stride were 8-way bank conflicts).  Lanes with bit 3 set read their second half
-      // first: each 16-lane group of a ds_read_b128 then covers all 64 banks (in one order the groups'
-      // lanes l and l + 8 or l + 24 met on a bank, 2-way: ~40 % of the kernel's cycles by SQ_LDS_BANK_CONFLICT)
-      float zz8[8], dd8[8], yy8[8];
-      {
-        const int o1 = (lane & 8) ? 4 : 0, o2 = 4 - o1;
-        const bool sw = lane & 8;
-        auto rd2 = [&](const float *base, float *dst) __attribute__((always_inline)) {
-          const float4 f1 = *(const float4 *)&base[q0 + o1];
-          const float4 f2 = *(const float4 *)&base[q0 + o2];
-          *(float4 *)&dst[0] = sw ? f2 : f1;
-          *(float4 *)&dst[4] = sw ? f1 : f2;
-        };
-        rd2(zdp, zz8);
-        rd2(zdp + n_pad, dd8);
-        rd2(zdp + 2 * n_pad, yy8);
-      }
-#pragma unroll
-      for (int h = 0; h < 8; ++h) {
-        const float av = (float)ca[h], bv = (float)cb[h], w = av * bv;  // exact small integers
-        const float z = zz8[h], d = dd8[h], y = yy8[h];
-        const float tu = be * uu[h], tv = al * vv[h], tz = ab * z;
-        s1 += w * ((tz - tu) - tv);
-        s1a += w * ((fabsf(tu) + fabsf(tv)) + fabsf(tz));
-        s2 += av * vv[h];
-        s2a += av * fabsf(vv[h]);
-        s3 += d * (w * w);
-        s3a += fabsf(d) * (w * w);
-        const float ey = ((av - al) * (bv - be)) * y;
-        ef += ey;
-        efa += fabsf(ey);
-        sw += w * w;
-      }
-    }
-    double r[9] = {s1, s1a, s2, s2a, s3, s3a, ef, efa, sw};
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) r[t] += __shfl_xor(r[t], off);
-    if (lane != 0) continue;
-    const double t3 = dbe * dbe * x.qa[i], t5 = dal * dal * x.qb[j], t7 = dab * dab * x.zz, t8 = 2.0 * dab * r[2],
-                 t4 = -2.0 * dab * dbe * x.ra[i], t6 = -2.0 * dab * dal * x.rb[j];
-    x.side[p] = r[4] + 2.0 * r[0] + t3 + t5 + t7 + t8 + t4 + t6;
-    // fp32 sums: a lane adds n_pad / 64 terms of at most 4 roundings each, so a sum is within
-    // (n_pad / 64 + 4) 2^-24 of its absolute sum (the lane reduction is fp64); fsl doubles that.  U is
-    // stored in fp16: a normal value is within 2^-11 of U, relative, so the U terms (su, their magnitudes
-    // from the rounded values) are within 2^-10.9 su; a subnormal one within 2^-25 absolute, at most
-    // 2^-25 (|alpha| + |beta|) 4 n_pad in total (an overflow gives inf / NaN: the pair is kept).  Plus
-    // the fp64 rounding of U = P x codes and of the host terms (far inside 1e-10 of the magnitudes).
-    // side[3 np + p] is the eff bound's slack.
-    const double fsl = 2.0 * (double)(n_pad / 64 + 8) * 0x1p-24;
-    const double su = 2.0 * r[1] + 2.0 * fabs(dab) * r[3];
-    x.side[x.np + p] = fsl * (su + r[5]) + 0x1p-10 * su + 0x1p-23 * (fabs(dal) + fabs(dbe)) * 4.0 * (double)n_pad +
-                       1e-10 * (r[5] + su + fabs(t3) + fabs(t5) + fabs(t7) + fabs(t4) + fabs(t6));
-    x.side[2 * x.np + p] = r[6];
-    x.side[3 * x.np + p] = (fsl + 1e-10) * r[7];
-    x.side[4 * x.np + p] = r[8];
+  const int64_t pw = ((int64_t)blockIdx.x * 4 + wv) * PS_PPW;  // the wave's candidates: pw .. pw + cnt - 1
+  if (pw >= x.np) return;
+  const int cnt = (int)min((int64_t)PS_PPW, x.np - pw);
+  int my_i = -1, my_j = 0;  // (SNP indices fit an int: m x n_pad panels are in memory)
+  if (lane < cnt) {
+    my_i = (int)x.ci[pw + lane];
+    my_j = (int)x.cj[pw + lane];
+  }
+  for (int k = 0; k < cnt;) {
+    const int i = __builtin_amdgcn_readfirstlane(__shfl(my_i, k));
+    int g = 1;
+    while (g < PS_G && k + g < cnt && __builtin_amdgcn_readfirstlane(__shfl(my_i, k + g)) == i) ++g;
+    if (PS_G >= 4 && g == 4)
+      pair_side_group<4>(x, zdp, lane, pw + k, i, my_j, k);
+    else if (PS_G >= 3 && g == 3)
+      pair_side_group<3>(x, zdp, lane, pw + k, i, my_j, k);
+    else if (g == 2)
+      pair_side_group<2>(x, zdp, lane, pw + k, i, my_j, k);
+    else
+      pair_side_group<1>(x, zdp, lane, pw + k, i, my_j, k);
+    k += g;
   }
 }
 

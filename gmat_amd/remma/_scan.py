@@ -95,6 +95,16 @@ class EpiPlan:
                 "gmat_epi_audit")
         return out
 
+    def pair_audit(self, kind, pairs):
+        """The pair screen's own numbers for the listed pairs, in the listed order (its kernels run on
+        the list as on a screen's candidates): columns (side, side_slack, eff, eff_slack, sum w^2,
+        var_lo, eff_hi).  With pairs()' exact values, var >= var_lo and |eff| <= eff_hi must hold."""
+        pairs = N.i64(np.asarray(pairs).reshape(-1, 2))
+        out = np.zeros((pairs.shape[0], 7))
+        N.check(self._lib.gmat_epi_pair_audit(self._h, KINDS[kind], N.ptr(pairs), pairs.shape[0], N.ptr(out)),
+                "gmat_epi_pair_audit")
+        return out
+
     def stats(self):
         s = np.zeros(10)
         N.check(self._lib.gmat_epi_stats(self._h, N.ptr(s)), "gmat_epi_stats")

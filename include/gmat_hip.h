@@ -147,6 +147,11 @@ int gmat_epi_kernel_stats_ext(const gmat_epi *e, double *out, int cap, int *coun
  * out5[5 t ..] = {prefilter bound, low-rank bound, |e|^2, 1'e, |Q'e|^2} (-inf where the plan has no
  * such screen).  Compared with the exact e'Pe of gmat_epi_pairs, every ratio must be >= 1. */
 int gmat_epi_audit(gmat_epi *e, int kind, const int64_t *pairs, int64_t n_pairs, double *out5);
+/* diagnostic: the pair screen's numbers for listed pairs (i, j), its kernels run on the list in the
+ * listed order: out7[7 t ..] = {side terms of var, their slack, eff, its slack, sum w^2, var_lo, eff_hi}
+ * as the screen's test forms them.  With the exact values of gmat_epi_pairs, var >= var_lo and
+ * |eff| <= eff_hi must hold (a NaN or -inf var_lo keeps the pair).  Not for plans split into segments. */
+int gmat_epi_pair_audit(gmat_epi *e, int kind, const int64_t *pairs, int64_t n_pairs, double *out7);
 /* screen certificates of the plan: [0] rank of the low-rank spectral screen (padded to 128; 0 =
  * none, scans use the fp6 quadratic form), [1] its lam, [2] the prefilter's mu, [3] n_pad; the
  * compacted scan's prefilter (prefilter_pass_kernel): [4] tile rows, [5] tile columns, [6] bytes one
